@@ -7,6 +7,7 @@ full-width fp32 proposal (4x256) + NeRF (8x1024) MLPs — BASELINE.json configs[
 weights are resident in HBM before the timed region.
 
   python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --full               # + roofline, frame leg, named workloads, CPU baseline and parity
   python bench.py --gpus 8                      # starts 8 fresh rank processes itself (torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N ...  # or launched from outside: RANK / LOCAL_RANK / WORLD_SIZE from the env
@@ -18,15 +19,28 @@ Nothing is ever exec'ed in place (`--dry-launch` prints the child command instea
 Default workload (c2, weak scaling): every rank renders its own 4096-ray batch (rays shard with no data-path
 collective) and the rendered pixels (20 B per ray) are all-gathered over RCCL each step, as the path's one exchange
 step.  Rank 0 prints ONE JSON line; for N > 1 it carries `rccl.ranks`, the world size read back from an all-reduce.
-After the timed region the same processes render ONE 1237 x 822 frame sharded over the N ranks at 64 proposal + 128 NeRF
-samples per ray (BASELINE configs[2] as written; configs[3] for N > 1, strong scaling; `strong_scaling_frame` in the line,
-`--frame-steps 0` to skip), and at N = 1 the process then times the other single-GPU workloads for a few steps each
-(`named_workloads`: configs[4]'s shape in bf16, configs[1] in bf16 and bf16x3, one train.py iteration; `--no-named` to skip).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR) and the
+line.  Everything else is measured with --full only:
+  * the per-kernel event records of the timed steps (`roofline`, `hbm_kernels`; bf16: the layer chain's counters, `chain`);
+  * c2: after the timed region the same processes render ONE 1237 x 822 frame sharded over the N ranks at 64 proposal + 128
+    NeRF samples per ray (BASELINE configs[2] as written; configs[3] for N > 1, strong scaling; `strong_scaling_frame` in the
+    line, `--frame-steps 0` to skip);
+  * c2 at N = 1: the other single-GPU workloads, a few steps each (`named_workloads`: configs[4]'s shape in bf16, configs[1]
+    in bf16 and bf16x3, one train.py iteration; `--no-named` to skip), and the CPU oracle on the same batch
+    (`cpu_baseline`, `parity`; `--cpu-rays 0` to skip);
+  * c4 at N > 1: the same frames again with a serial gather (`frame.serial`).
+--frame-steps and --cpu-rays given explicitly run their legs in a plain run too.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its last step as DIR/<name>.npy
+(float32): rgb.npy, distance.npy, acc.npy - the forward's outputs at N = 1, the all-gathered pixels of all ranks at N > 1,
+the assembled last frame for c4.  Inputs are seeded, so two builds run with the same arguments can be compared array for
+array.  Above 64 MB in all, a fixed seeded sample of rays is written, with its ray indices as sample_index.npy (float64).
 
 Other named workloads (never the default line):
   --config c4          BASELINE configs[3] as the timed workload: frames of 1237 x 822 rays, each rank generates and
                        renders the rays of its own block of 4096-ray chunks, one pixel all-gather per frame, overlapped
-                       with the next frame's compute on a side stream (the serial numbers are reported beside it);
+                       with the next frame's compute on a side stream (--full: the serial numbers beside it);
   --config c5          BASELINE configs[4]'s per-GPU shape (8192 rays x 256 samples, bf16 MLP);
   --mlp-dtype bf16     configs[1] with the opt-in bf16 MLP.
   --backend gloo       (diagnostics) ranks may share a GPU, collectives staged through the host: exercises the launcher
@@ -115,21 +129,21 @@ def parse_args(argv=None):
                     help="c2 = the headline workload (BASELINE configs[1]); c4 = one frame sharded over the GPUs "
                          "(configs[3], strong scaling); c5 = BASELINE configs[4]'s shape (bf16)")
     ap.add_argument("--cpu-rays", type=int, default=None,
-                    help="rays of the batch timed on the host CPU (default: the whole 4096-ray batch for c2, 0 = skip)")
+                    help="rays of the batch timed on the host CPU (default with --full: the whole 4096-ray batch for c2; 0 = skip)")
     ap.add_argument("--mlp-dtype", choices=("fp32", "bf16", "bf16x3"), default=None,
                     help="override the workload's MLP precision (c2: fp32 = the headline; bf16 = opt-in reduced-precision "
                          "MLP, reported with dtype bf16 and never comparable to the fp32 line; bf16x3 = two bf16 terms per "
                          "value, three MFMA passes per product: inside the fp32 render tolerance, reported with dtype bf16x3)")
     ap.add_argument("--frame-steps", type=int, default=None,
                     help="c2 only: frames of the 1237x822 strong-scaling workload rendered AFTER the timed region and "
-                         "reported as `strong_scaling_frame` (default 1; 0 = skip)")
+                         "reported as `strong_scaling_frame` (default 1 with --full, else 0; 0 = skip)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="nccl = RCCL (the product); gloo = diagnostics only (ranks may share a GPU, host-staged collectives)")
     ap.add_argument("--frame-size", type=str, default=None, metavar="WxH",
                     help="(diagnostics) frame size of the c4 workload / strong_scaling_frame instead of 1237x822; the line "
                          "then says so in config.workload")
     ap.add_argument("--no-named", action="store_true",
-                    help="c2 / fp32 / 1 GPU only: skip the `named_workloads` block (the other single-GPU configs, a few steps each)")
+                    help="--full, c2 / fp32 / 1 GPU only: skip the `named_workloads` block (the other single-GPU configs, a few steps each)")
     ap.add_argument("--no-chain", action="store_true", help="(diagnostics, bf16 mode) M360_TUNE_NO_HIDDEN_CHAIN per call: six launches for the six hidden NeRF layers")
     ap.add_argument("--plain-rows", action="store_true",
                     help="(diagnostics, bf16 modes) M360_TUNE_PLAIN_ROWS per call: plain instead of paired rows between the layers - same bits; "
@@ -139,6 +153,11 @@ def parse_args(argv=None):
                          "waiting in a collective) and the run must still end with its headline line and rc 0")
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 and no WORLD_SIZE: print the child command as JSON and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel roofline / HBM figures, the frame leg, the named "
+                         "workloads, the CPU oracle baseline and parity (a plain run only times the headline)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the timed path's outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB)")
     return ap.parse_args(argv)
 
 
@@ -467,6 +486,25 @@ def chain_delta(model, before=None):
     return d
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: (rgb[n,3], distance[n], acc[n]) of the timed path -> DIR/rgb.npy, distance.npy, acc.npy in float32.
+    Above DUMP_BYTES_MAX in all, the same fixed seeded sample of rays from each, and its ray indices as sample_index.npy."""
+    import numpy as np
+    arrays = {k: t.detach().float().cpu().numpy() for k, t in zip(("rgb", "distance", "acc"), outputs)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        n = len(arrays["acc"])
+        idx = np.sort(np.random.default_rng(0).choice(n, n * DUMP_BYTES_MAX // total, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 MLP_NAMES = {"fp32": "fp32", "bf16": "bf16 (fp32 accumulate)",
              "bf16x3": "bf16x3 (two bf16 terms per value, xh wh + xl wh + xh wl on the bf16 MFMA, fp32 accumulate)"}
 FRAME_POSE = [[1.0, 0.0, 0.0, 0.05], [0.0, 1.0, 0.0, -0.02], [0.0, 0.0, 1.0, 0.1]]
@@ -484,7 +522,7 @@ def frame_pipeline(model, comm, frames, warmup, overlap, width=FRAME_W, height=F
     its own block of chunks (m360_generate_rays_span), renders them into the send block of a PixelGather and the
     pixels are all-gathered.  overlap=True: the all-gather + assembly of frame i run on a side stream under the compute
     of frame i + 1 (two send / receive slots); overlap=False: everything on one stream.
-    -> dict with wall seconds (max over ranks) and per-rank medians."""
+    -> ((rgb, distance, acc) of the last assembled frame, dict with wall seconds (max over ranks) and per-rank medians)."""
     import torch
 
     from mipnerf360_amd.distributed import PixelGather, partition_efficiency, render_local_block
@@ -543,7 +581,7 @@ def frame_pipeline(model, comm, frames, warmup, overlap, width=FRAME_W, height=F
     # the assembled last frame as one number (sum of the pixels' bit patterns): overlapped == serial == one rank, bit for bit
     bits_sum = int(sum(int(t.contiguous().view(torch.int32).to(torch.int64).sum()) for t in last))
     n_chunks = (n + chunks - 1) // chunks
-    return {"frames": frames, "rays_per_frame": n, "seconds": round(elapsed, 4), "seconds_per_frame": round(elapsed / max(frames, 1), 4),
+    return last, {"frames": frames, "rays_per_frame": n, "seconds": round(elapsed, 4), "seconds_per_frame": round(elapsed / max(frames, 1), 4),
             "rays_per_s": round(n * frames / elapsed, 1), "n_chunks": n_chunks,
             "chunks_per_rank": (n_chunks + world - 1) // world,
             "partition_efficiency_bound": round(partition_efficiency(n, chunks, world), 4),
@@ -573,7 +611,7 @@ def timed_forward(model, rays, steps, warm, _lib, torch):
 
 def named_workloads(sd_np, dev, _lib):
     """The other single-GPU configurations of BASELINE.json, timed in this process after the headline's timed region, a few
-    steps each: the driver's default run then carries a number for every single-GPU config.  Every entry
+    steps each: a --full run then carries a number for every single-GPU config.  Every entry
     has its own dtype, rays/s, ms/step and the dominant kernel's roofline fraction from HIP-event records of its own steps.
     None of this touches the headline fields."""
     import torch
@@ -778,9 +816,9 @@ def worker(args):
     steps = args.steps if args.steps is not None else (3 if frame_cfg else 50)
     warmup = args.warmup if args.warmup is not None else (1 if frame_cfg else 5)
     if args.cpu_rays is None:
-        args.cpu_rays = n_rays if (args.config == "c2" and mlp_dtype != "bf16") else 0
+        args.cpu_rays = n_rays if (args.full and args.config == "c2" and mlp_dtype != "bf16") else 0
     if args.frame_steps is None:
-        args.frame_steps = 1 if (args.config == "c2" and mlp_dtype == "fp32") else 0
+        args.frame_steps = 1 if (args.full and args.config == "c2" and mlp_dtype == "fp32") else 0
 
     import numpy as np
     import torch
@@ -820,7 +858,7 @@ def worker(args):
         from mipnerf360_amd.distributed import check_replicas
         check_replicas(model)  # one 32-byte all-reduce at setup: every rank holds the same weights / sample counts
 
-    chain0 = chain_delta(model)
+    chain0 = chain_delta(model) if args.full else None
     line = {"metric": metric, "value": None, "unit": "rays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": None, "higher_is_better": True, "scaling": "strong" if frame_cfg else "weak",
             "vs_baseline": None, "dtype": mlp_dtype if bf16 else "f32", "data": "synthetic"}
@@ -832,12 +870,14 @@ def worker(args):
         fw, fh = frame_size(args)
         n_frame = fw * fh
         chunks_mine = (n_frame + FRAME_CHUNKS - 1) // FRAME_CHUNKS
-        prof = _lib.Prof(40 * (chunks_mine // world + 2) * (steps + warmup) * 2 + 64)
-        model.set_prof(prof)
-        res = frame_pipeline(model, comm, steps, warmup, overlap=True, width=fw, height=fh)
+        if args.full:
+            prof = _lib.Prof(40 * (chunks_mine // world + 2) * (steps + warmup) * 2 + 64)
+            model.set_prof(prof)
+        last, res = frame_pipeline(model, comm, steps, warmup, overlap=True, width=fw, height=fh)
         model.set_prof(None)
-        recs = prof.records()
-        serial = frame_pipeline(model, comm, steps, warmup, overlap=False, width=fw, height=fh) if world > 1 else None
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)
+        serial = frame_pipeline(model, comm, steps, warmup, overlap=False, width=fw, height=fh)[1] if (args.full and world > 1) else None
         if args.frame_size:
             workload = f"DIAGNOSTIC frame size {fw}x{fh} instead of 1237x822; " + workload
         elapsed = res["seconds"]
@@ -879,8 +919,9 @@ def worker(args):
 
         for _ in range(warmup):
             step()
-        prof = _lib.Prof(48 * max(steps, 1))  # caller-owned HIP-event recorder: every kernel of the stage drivers
-        model.set_prof(prof)
+        if args.full:
+            prof = _lib.Prof(48 * max(steps, 1))  # caller-owned HIP-event recorder: every kernel of the stage drivers
+            model.set_prof(prof)
         comm.fence()
         t0 = time.perf_counter()
         out = None
@@ -898,7 +939,8 @@ def worker(args):
             allr = comm.gather_floats([statistics.median(compute_ms), statistics.median(gather_ms)])
             per_rank = [{"rank": r, "compute_ms_median": round(t[0], 3), "all_gather_ms_median": round(t[1], 3)}
                         for r, t in enumerate(allr)]
-        recs = prof.records()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out if pg is None else pg.assemble())  # N > 1: the pixels of all ranks, as gathered
         value = world * n_rays * steps / elapsed
         med_ms = statistics.median(step_ms) if step_ms else 0.0
         line.update(value=round(value, 1), ms_per_step=round(1e3 * elapsed / max(steps, 1), 3),
@@ -918,11 +960,13 @@ def worker(args):
             line["per_rank"] = per_rank
 
     # ---- per-kernel numbers from the event records (HIP events on the launch stream, inside the timed region)
-    prof.close()
-    line["roofline"] = roofline_from_records(recs, S, bf16, args.config, _lib, x3)
+    if prof is not None:
+        recs = prof.records()
+        prof.close()
+        line["roofline"] = roofline_from_records(recs, S, bf16, args.config, _lib, x3)
+        line["hbm_kernels"] = hbm_kernels_from_records(recs, n_rays, samples, bf16, _lib, x3)
     if chain0 is not None:  # bf16 mode: what the layer chain's self-checks saw over warm-up + timed region (this rank)
         line["chain"] = chain_delta(model, chain0)
-    line["hbm_kernels"] = hbm_kernels_from_records(recs, n_rays, samples, bf16, _lib, x3)
     line["rccl"] = comm.info
 
     if not frame_cfg and args.frame_steps > 0:
@@ -952,7 +996,7 @@ def worker(args):
 
         def frame_leg():
             fmodel.set_prof(fprof)
-            fr = frame_pipeline(fmodel, comm, args.frame_steps, 0, overlap=False, width=fw, height=fh)
+            _, fr = frame_pipeline(fmodel, comm, args.frame_steps, 0, overlap=False, width=fw, height=fh)
             fmodel.set_prof(None)
             frecs = fprof.records()
             fprof.close()
@@ -983,7 +1027,7 @@ def worker(args):
         comm.close()
         return
 
-    if args.config == "c2" and mlp_dtype == "fp32" and world == 1 and not args.no_named:
+    if args.full and args.config == "c2" and mlp_dtype == "fp32" and world == 1 and not args.no_named:
         line["named_workloads"] = named_workloads(sd_np, dev, _lib)
         if "strong_scaling_frame" in line and "error" not in line["strong_scaling_frame"]:  # BASELINE configs[2] is the frame leg above: listed with the others
             fr = line["strong_scaling_frame"]

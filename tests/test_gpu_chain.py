@@ -327,9 +327,9 @@ def test_bf16_frames_over_two_ranks_with_the_overlapped_gather(dev):
     (every chunk's NeRF MLP through the chain) while the pixel gather of the previous frame runs on a side stream.  The assembled frame
     must be the SAME BITS overlapped, serial, and rendered by one rank alone; the line carries the chain's counters."""
     size = "300x205"  # 61500 rays: 16 chunks of 4096 (the last one partial)
-    res2, two = _run_bench("--gpus", "2", "--backend", "gloo", "--config", "c4", "--mlp-dtype", "bf16", "--steps", "3", "--warmup", "1", "--frame-size", size)
+    res2, two = _run_bench("--gpus", "2", "--backend", "gloo", "--config", "c4", "--mlp-dtype", "bf16", "--steps", "3", "--warmup", "1", "--frame-size", size, "--full")
     assert res2.returncode == 0 and two is not None, (res2.stdout[-1500:], res2.stderr[-3000:])
-    res1, one = _run_bench("--config", "c4", "--mlp-dtype", "bf16", "--steps", "1", "--warmup", "1", "--frame-size", size)
+    res1, one = _run_bench("--config", "c4", "--mlp-dtype", "bf16", "--steps", "1", "--warmup", "1", "--frame-size", size, "--full")
     assert res1.returncode == 0 and one is not None, (res1.stdout[-1500:], res1.stderr[-3000:])
     assert two["dtype"] == "bf16" and two["frame"]["overlapped"]["overlap"] and not two["frame"]["serial"]["overlap"]
     sums = {two["frame"]["overlapped"]["frame_bits_sum"], two["frame"]["serial"]["frame_bits_sum"], one["frame"]["overlapped"]["frame_bits_sum"]}

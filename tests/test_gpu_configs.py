@@ -155,7 +155,8 @@ def test_c5_full_size_fp32_properties(dev):
 
 def test_bench_c5_named_workload(dev):
     """`bench.py --config c5`: the configs[4] shape as a named bench workload (dtype bf16), never the default line."""
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c5", "--steps", "3", "--warmup", "1"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c5", "--steps", "3", "--warmup", "1",
+                          "--full"],
                          cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -256,7 +257,7 @@ def test_bench_launches_its_own_ranks_weak_scaling_line(dev):
     processes, rank 0's single JSON line comes back through the parent.  One GPU here, so the diagnostics backend (gloo,
     ranks share cuda:0) stands in for RCCL: launcher, per-rank batches, PixelGather, replica check and the
     strong_scaling_frame leg are the production code."""
-    res, line = _run_bench("--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--frame-size", "160x120")
+    res, line = _run_bench("--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--frame-size", "160x120", "--full")
     assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
     assert len([ln for ln in res.stdout.splitlines() if ln.strip()]) == 1, "exactly ONE line on stdout"
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["scaling"] == "weak" and line["dtype"] == "f32"
@@ -274,7 +275,7 @@ def test_bench_eight_ranks_share_the_gpu_over_gloo(dev):
     """The driver's N = 8 invocation (`python bench.py --gpus 8`), as far as ONE GPU can go: eight fresh rank processes through bench.py's own
     launcher, each with its own 4096 x 128 batch (weak line) and its block of whole chunks of one frame (configs[3]: 30 chunks -> 4 per rank,
     the last rank 2), pixel blocks gathered over gloo - the per-rank code, partition and gather logic of the RCCL run; no performance claim."""
-    res, line = _run_bench("--gpus", "8", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--frame-size", "400x300", timeout=900)
+    res, line = _run_bench("--gpus", "8", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--frame-size", "400x300", "--full", timeout=900)
     assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
     assert line["n_gpus"] == 8 and line["rccl"]["ranks"] == 8 and len(line["per_rank"]) == 8 and line["scaling"] == "weak"
     assert line["config"]["global_rays"] == 8 * 4096 if "global_rays" in line["config"] else True
@@ -291,7 +292,7 @@ def test_bench_frame_leg_is_skipped_by_all_ranks_when_one_cannot_set_it_up(dev, 
     MIN all-reduce everybody takes part in) before the leg's first collective: either rank failing makes BOTH skip it, the run ends with
     its headline line and rc 0, within the timeout."""
     res, line = _run_bench("--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--frame-size", "160x120",
-                           "--fail-frame-setup-on-rank", str(bad_rank), timeout=420)
+                           "--fail-frame-setup-on-rank", str(bad_rank), "--full", timeout=420)
     assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
     assert line["value"] > 0 and line["n_gpus"] == 2
     assert "error" in line["strong_scaling_frame"] and "rays_per_s" not in line["strong_scaling_frame"], line["strong_scaling_frame"]
@@ -303,7 +304,7 @@ def test_bench_c4_frames_sharded_over_two_ranks(dev):
     """bench.py --config c4 (BASELINE configs[3]) through its own launcher: frames sharded by whole chunks, each rank
     generating the rays of its own span, overlapped and serial pixel gathers."""
     res, line = _run_bench("--gpus", "2", "--backend", "gloo", "--config", "c4", "--steps", "3", "--warmup", "1",
-                           "--frame-size", "200x123")
+                           "--frame-size", "200x123", "--full")
     assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
     n = 200 * 123
     assert line["scaling"] == "strong" and line["n_gpus"] == 2 and line["config"]["name"] == "c4"
@@ -442,11 +443,11 @@ def test_grouped_chunks_bit_identical_at_fusable_widths(dev):
 
 
 def test_bench_default_line_carries_every_single_gpu_config(dev):
-    """the DEFAULT `python bench.py` line (what the driver records) carries a number for every single-GPU
+    """the `python bench.py --full` line (the default line before --full) carries a number for every single-GPU
     configuration of BASELINE.json - the headline (configs[1], fp32) untouched, `strong_scaling_frame` at 64 proposal + 128 NeRF samples
     (configs[2] as written; here a small diagnostic frame), and `named_workloads`: configs[4]'s shape in bf16, configs[1] in bf16 and
     bf16x3, one train.py iteration - each with its own dtype, rays/s, ms/step and roofline fraction.  (Short: 3 steps, no CPU pass.)"""
-    res, line = _run_bench("--steps", "3", "--warmup", "1", "--cpu-rays", "0", "--frame-size", "200x160")
+    res, line = _run_bench("--steps", "3", "--warmup", "1", "--cpu-rays", "0", "--frame-size", "200x160", "--full")
     assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
     assert line["dtype"] == "f32" and line["config"]["name"] == "c2" and line["n_gpus"] == 1 and line["vs_baseline"] is None
     assert line["metric"] == "rendered rays/sec at 128 samples/ray" and line["unit"] == "rays/s" and line["higher_is_better"] is True
@@ -473,3 +474,29 @@ def test_bench_default_line_carries_every_single_gpu_config(dev):
     fr128 = nw["c1_frame_chunks128"]        # the reference's CLI default chunk size, through the grouped-chunk path
     assert fr128["finite"] and fr128["chunks"] == 128 and fr128["rays_per_s"] > 5e4
     assert nw["seconds"] < 45
+
+
+def test_bench_plain_line_times_the_headline_and_dumps_its_outputs(dev, tmp_path):
+    """A plain `bench.py` run (no --full) times the headline alone: --steps steps, the headline fields, none of the extra legs.  With
+    --dump-outputs it writes the outputs of its last timed step, and they are the public forward's outputs on bench.py's batch
+    (seed-0 weights, seed-1 rays, 4096 x 128, full width), bit for bit."""
+    from mipnerf360_amd.model import mipNeRF360
+    out = tmp_path / "outputs"
+    res, line = _run_bench("--steps", "4", "--warmup", "1", "--dump-outputs", str(out))
+    assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
+    assert line["metric"] == "rendered rays/sec at 128 samples/ray" and line["unit"] == "rays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["steps"] == 4 and line["warmup"] == 1 and line["value"] > 6e4
+    assert abs(line["ms_per_step"] - 4096 / line["value"] * 1e3) < 0.01 * line["ms_per_step"]
+    for k in ("roofline", "hbm_kernels", "strong_scaling_frame", "named_workloads", "cpu_baseline", "parity"):
+        assert k not in line, k
+    got = {k: np.load(out / f"{k}.npy") for k in ("rgb", "distance", "acc")}
+    assert sorted(p.name for p in out.iterdir()) == ["acc.npy", "distance.npy", "rgb.npy"]
+    assert got["rgb"].shape == (4096, 3) and got["distance"].shape == got["acc"].shape == (4096,)
+    assert all(a.dtype == np.float32 for a in got.values())
+    m = mipNeRF360(randomized=False, num_samples=128, hidden_proposal=256, hidden_nerf=1024, white_bkgd=False, device=dev)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic.make_state_dict(256, 1024, seed=0).items()})
+    m.eval()
+    with torch.no_grad():
+        want = [t.cpu().numpy() for t in m(dev_rays(synthetic.make_rays("garden", 4096, seed=1), dev))]
+    for k, w in zip(("rgb", "distance", "acc"), want):
+        assert np.array_equal(got[k], w), k

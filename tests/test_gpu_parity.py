@@ -1453,7 +1453,7 @@ def test_rccl_path_single_rank_torchrun(dev):
     assert res.returncode == 0 and "sharded==single: True" in res.stdout, res.stdout[-2000:]
     assert "forward_sharded max |diff| vs whole-batch forward: 0.00e+00" in res.stdout, res.stdout[-2000:]
     res = subprocess.run(base + ["29542", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                                 "--cpu-rays", "0"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                                 "--cpu-rays", "0", "--full"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                          text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:]
     import json

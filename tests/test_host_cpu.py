@@ -627,6 +627,35 @@ def test_bench_preflight_counts_gpus_without_touching_them(tmp_path, monkeypatch
     assert bench.launch(args, ["--gpus", "4", "--dry-launch"]) == 0       # printing the command needs no GPU
 
 
+def test_bench_dump_outputs_writes_float32_arrays_and_samples_above_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: rgb / distance / acc as float32 .npy files; above the size cap the same fixed seeded sample of rays
+    from each array, with its ray indices.  A plain run measures the headline only: --full is off by default."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    assert bench.parse_args(["--full", "--dump-outputs", "x"]).full is True
+    n = 1000
+    rgb = torch.arange(3 * n, dtype=torch.float64).view(n, 3)
+    dist, acc = torch.arange(n, dtype=torch.float32) + 0.5, torch.linspace(0, 1, n)
+    bench.dump_outputs(str(tmp_path / "all"), (rgb, dist, acc))
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("rgb", "distance", "acc")}
+    assert sorted(p.name for p in (tmp_path / "all").iterdir()) == ["acc.npy", "distance.npy", "rgb.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["rgb"], rgb.float().numpy()) and np.array_equal(got["distance"], dist.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 5 * 4 * 100)               # room for 100 of the 1000 rays
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), (rgb, dist, acc))
+    files = ("rgb", "distance", "acc", "sample_index")
+    s1, s2 = ({k: np.load(tmp_path / d / f"{k}.npy") for k in files} for d in ("s1", "s2"))
+    idx = s1["sample_index"]
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert all(np.array_equal(s1[k], s2[k]) for k in files)                 # the same sample every time
+    assert np.array_equal(s1["rgb"], got["rgb"][idx.astype(np.int64)]) and np.array_equal(s1["acc"], got["acc"][idx.astype(np.int64)])
+
+
 def test_dropin_falls_through_to_reference_helpers(tmp_path):
     """install_dropin(reference_root=...): modules without a mirror (intern.scheduler) and names missing from a mirror
     (camera paths of intern.pose, intern.utils.normalize) resolve to the reference's own files; mirrored names win.

@@ -247,7 +247,7 @@ def readme_state(tag):
         return f"*(no profiles/{tag}/bench.json)*\n"
     r, nw, p_ = b["roofline"], b.get("named_workloads", {}), b.get("parity", {})
     f_ = b.get("strong_scaling_frame", {})
-    parts = [f"*Generated by `python tools/summarize_profiles.py --readme {tag}` from `profiles/{tag}/bench.json` (one default `python bench.py` run on 1 x MI355X; "
+    parts = [f"*Generated by `python tools/summarize_profiles.py --readme {tag}` from `profiles/{tag}/bench.json` (one `python bench.py --full` run on 1 x MI355X; "
              f"boxes of the pool differ by +-2 %).*", "",
              f"fp32 headline (BASELINE configs[1], 4096 rays x 128 samples): **{b['value'] / 1e3:.1f} k rays/s**, {b['ms_per_step']:.2f} ms per step = "
              f"{100 * b['config']['whole_path_tflops'] / r['peak']:.1f} % of the fp32 matrix-core roofline for the whole forward; dominant kernel "
